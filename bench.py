@@ -9,10 +9,18 @@ resident in HBM to the finished implicit in-order tree (ids + coordinates) in HB
   generation-order slice (the reference's MPI slicing, kdtree_mpi.cpp:204-224); the top
   levels are split with allreduced histograms, points are redistributed with all-to-all
   rounds, and each GPU builds its leaves' subtrees (csrc/cpu/global_builder.cpp). Strong
-  scaling: the total point count is fixed, so `value` is the whole-job throughput. After the
-  timed loop rank 0 prints the per-phase breakdown of one extra (untimed, profiled) build on
-  stderr -- top levels, pack, plan wait, exchange (bytes, GB/s), id rebuild, leaf builds --
-  as the MAX over ranks.
+  scaling: the total point count is fixed, so `value` is the whole-job throughput. With --full,
+  after the timed loop rank 0 prints the per-phase breakdown of one extra (untimed, profiled)
+  build on stderr -- top levels, pack, plan wait, exchange (bytes, GB/s), id rebuild, leaf
+  builds -- as the MAX over ranks.
+
+A plain run sets up, warms up, times --steps builds, reads the builds' error words and prints
+the result line. --full adds what takes runs or passes of its own: the untimed check of the
+last tree and the per-phase breakdown build. --dump-outputs DIR writes the last timed build's
+tree (tree_pts.npy float32, tree_ids.npy float64; above 64 MB the same seeded sample of slots
+of both, listed in sample_rows.npy) so that two builds of the project can be compared; on the
+distributed path every rank writes its share (<name>_rank<r>.npy at N > 1) and rank 0 the top-tree
+rows (top_pts.npy, top_ids.npy, top_slots.npy).
 
 Launch: under torch.distributed.run (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the env), or
 plain `python bench.py --gpus N`: without WORLD_SIZE the process becomes a launcher that never
@@ -21,16 +29,17 @@ with the first failing rank's status.
 
 Data: the reference generator stream (std::mt19937 + uniform_real<float>(-100,100), seed 42),
 each rank's slice generated on its own GPU by the device generator (csrc/gpu/generator.hip,
-bit-identical to the host stream; untimed). After the timed loop (untimed) the last tree is
-checked: device error word, kd invariant on every node, ids a permutation (N = 1: the error
-words of EVERY timed build are folded on the device; a build whose sampled band missed is charged
-its unsampled rebuild); at N > 1 also
+bit-identical to the host stream; untimed). After the timed loop (untimed) the device error
+word is read (N = 1: the error words of EVERY timed build are folded on the device; a build whose
+sampled band missed is charged its unsampled rebuild). With --full the last tree is checked too:
+kd invariant on every node, ids a permutation; at N > 1 also
 every block of every rank against every top-tree pivot above it (cross-rank routing).
 Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
 
 import argparse
+import errno
 import json
 import os
 import socket
@@ -71,7 +80,13 @@ def _parse(argv=None):
     ap.add_argument("--device", choices=["cuda", "cpu"], default="cuda",
                     help="cpu: run the same control flow on host tensors over gloo (launcher / CI check; "
                          "timings meaningless)")
-    ap.add_argument("--no-check", action="store_true", help="skip the untimed correctness check of the last tree")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline timing: the untimed correctness check of the last tree and, on the "
+                         "native global path, the per-phase breakdown of one extra profiled build")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed build's tree (coordinates and ids, a fixed "
+                         "seeded sample of rows above 64 MB) as DIR/<name>.npy")
+    ap.add_argument("--no-check", action="store_true", help="--full: skip the untimed correctness check of the last tree")
     ap.add_argument("--decomp", choices=["auto", "single", "global"], default="auto",
                     help="auto: one GPU builds alone, N > 1 GPUs build one global tree; global also at N = 1 "
                          "(the multi-GPU code path on one rank)")
@@ -79,21 +94,41 @@ def _parse(argv=None):
                     help="global: extra top levels (leaves per rank = 2^k at power-of-two N; -1: auto)")
     ap.add_argument("--timeout", type=float, default=300.0,
                     help="global: bound of every host wait on the communicator (s); a stuck peer raises")
-    ap.add_argument("--no-profile", action="store_true", help="N > 1: skip the per-phase breakdown build")
+    ap.add_argument("--no-profile", action="store_true", help="--full, N > 1: skip the per-phase breakdown build")
     return ap.parse_args(argv)
 
 
-def _ensure_built(who: str) -> None:
-    """Bring the in-tree extension / executables up to date (file-locked, no GPU involved).
-    PKD_BENCH_TRACE_BUILD=1 reports on stderr what this process compiled and how long it took."""
+def _tree_writable() -> bool:
+    d = os.path.join(ROOT, "build")
+    return os.access(d if os.path.isdir(d) else ROOT, os.W_OK)
+
+
+def _ensure_built(who: str) -> bool:
+    """Bring the in-tree extension / executables up to date (file-locked, no GPU involved); True
+    when that was done, False when the build was not checked (the result line says so in
+    config.build_checked). PKD_BENCH_TRACE_BUILD=1 reports on stderr what this process compiled
+    and how long it took."""
     if os.environ.get("PKD_SKIP_BUILD") == "1":
-        return
+        return False
     from parallel_kd_tree_amd import _build
-    _build.build()
+    try:
+        _build.build()
+    except OSError as e:
+        if e.errno not in (errno.EACCES, errno.EPERM, errno.EROFS) or _tree_writable():
+            raise
+        # The tree cannot be written from this process (built by another user, or mounted read-only):
+        # nothing can be locked or compiled here, so what is built is run as it is, and the run says
+        # so. The extension must be there -- a missing one is an error, there is no other path.
+        from parallel_kd_tree_amd.ops import native
+        native()
+        print(f"bench.py: {who}: build NOT checked, the tree is read-only ({e}); running the extension as built",
+              file=sys.stderr, flush=True)
+        return False
     if os.environ.get("PKD_BENCH_TRACE_BUILD") == "1":
         lb = _build.LAST_BUILD
         what = ",".join(lb["compiled"]) if lb["compiled"] else "up to date"
         print(f"bench.py: {who}: build {what} ({lb['seconds'] * 1e3:.0f} ms)", file=sys.stderr, flush=True)
+    return True
 
 
 def _free_port() -> int:
@@ -188,6 +223,33 @@ def _distinct_ids(ids, n: int) -> str:
     return "duplicate ids" if int(seen.max()) > 1 else ""
 
 
+DUMP_BYTES = 64 * 1000 * 1000  # --dump-outputs writes at most this much, over all files and ranks
+DUMP_SEED = 20240229
+
+
+def _dump_outputs(out_dir: str, arrays: dict, suffix: str, budget: int) -> None:
+    """Write `arrays` (name -> tensor, all with the same number of rows) as out_dir/<name><suffix>.npy:
+    floating-point tensors as float32, integer ones as float64 (exact for 32-bit ids). Row i of
+    every file is the same tree slot. When the whole output is larger than `budget` bytes, a fixed
+    sample of rows is written instead (sorted slots drawn with replacement by a host generator seeded
+    with DUMP_SEED, so they depend only on the row count) and the slots go to sample_rows<suffix>.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    rows = next(iter(arrays.values())).shape[0]
+    conv = {k: (torch.float32 if v.is_floating_point() else torch.float64) for k, v in arrays.items()}
+    row_bytes = sum((v.numel() // max(rows, 1)) * (4 if conv[k] == torch.float32 else 8) for k, v in arrays.items())
+    pick, header = None, 128  # bytes of a .npy header
+    if rows * row_bytes + header * len(arrays) > budget:
+        k = max(budget - header * (len(arrays) + 1), 0) // (row_bytes + 8)
+        g = torch.Generator().manual_seed(DUMP_SEED)
+        pick = torch.randint(0, rows, (k,), generator=g).sort().values
+        np.save(os.path.join(out_dir, f"sample_rows{suffix}.npy"), pick.to(torch.float64).numpy())
+    for name, v in arrays.items():
+        if pick is not None:
+            v = v.index_select(0, pick.to(v.device))
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), v.to(conv[name]).cpu().contiguous().numpy())
+
+
 def main(argv=None):
     args = _parse(argv)
     world_env = os.environ.get("WORLD_SIZE")
@@ -223,7 +285,7 @@ def main(argv=None):
     # Every rank checks the in-tree build BEFORE joining the communicator: under torchrun there
     # is no launcher of ours, so the first rank to take the build lock compiles (if anything is
     # stale) and the rest find the signatures up to date; nobody waits inside a collective.
-    _ensure_built(f"rank {rank}")
+    build_checked = _ensure_built(f"rank {rank}")
     from parallel_kd_tree_amd.parallel import comm
     if world > 1:
         comm.init(backend="gloo" if cpu else os.environ.get("PKD_BENCH_BACKEND", "nccl"), device=dev)
@@ -301,14 +363,15 @@ def main(argv=None):
     if world > 1:
         dt = comm.max_float(dt)
 
-    # ---- untimed: the last build's tree must be right --------------------------------
+    # ---- untimed: the builds' error words; with --full the last build's tree must be right ----
+    check = args.full and not args.no_check
     problem = ""
     if distributed:
         err = builder.read_error() if not cpu else 0
         t = res["t"]
         if err:
             problem = f"device build reported error flags {err}"
-        elif not args.no_check:
+        elif check:
             problem = _check_share(t, n)
             if not problem:
                 idl = t.tree_ids.to(torch.int64) & 0xFFFFFFFF
@@ -323,7 +386,7 @@ def main(argv=None):
                     problem = f"the distributed tree holds {cnt} points (id sum {tot}) for ids 1..{n}"
     elif cpu:
         tp, ti = res["t"]
-        problem = "" if args.no_check else _check_tree(tp, ti + 1, 0, 1, n + 1)
+        problem = _check_tree(tp, ti + 1, 0, 1, n + 1) if check else ""
     else:
         acc = [int(v) & 0xFFFFFFFF for v in err_acc.tolist()]
         if acc[0] & ~GpuTreeBuilder.TOP_BAND_MISS:
@@ -348,7 +411,7 @@ def main(argv=None):
                   f"rebuilds are included in the timing", file=sys.stderr, flush=True)
             if b.read_error() & GpuTreeBuilder.TOP_BAND_MISS:
                 out_pts, out_ids = fb_pts, fb_ids
-        if not problem and not args.no_check:
+        if not problem and check:
             problem = _check_tree(out_pts, out_ids, 0, 1, n + 1)
     if world > 1:
         bad = torch.tensor([1 if problem else 0], dtype=torch.int64, device=dev)
@@ -361,8 +424,28 @@ def main(argv=None):
             comm.destroy()
         sys.exit(3)
 
-    # ---- untimed: where one build's time goes (N > 1, native): one profiled build -------
-    if distributed and not cpu and not args.no_profile:
+    # ---- untimed: what the last timed build computed, for comparing two builds of the project ----
+    if args.dump_outputs:
+        budget = DUMP_BYTES
+        if distributed:
+            outs = {"tree_pts": t.tree_pts, "tree_ids": t.tree_ids}
+            # the top-tree rows (heap order; replicated, so rank 0 writes them) and their global slots
+            # (-1: the row lies inside a rank's share); a few rows, written whole out of the budget
+            top = t.top_rows if t.top_rows is not None else torch.zeros((0, dim + 1))
+            top = top.detach().cpu().contiguous()
+            tops = {"top_pts": top[:, :dim], "top_ids": top[:, dim:].contiguous().view(torch.int32).reshape(-1),
+                    "top_slots": torch.tensor(list(t.top_slots)[:top.shape[0]], dtype=torch.int64)}
+            budget -= top.shape[0] * (4 * dim + 16) + 3 * 128
+            if rank == 0:
+                _dump_outputs(args.dump_outputs, tops, "", DUMP_BYTES)
+        elif cpu:
+            outs = {"tree_pts": tp, "tree_ids": ti}
+        else:
+            outs = {"tree_pts": out_pts, "tree_ids": out_ids}
+        _dump_outputs(args.dump_outputs, outs, f"_rank{rank}" if world > 1 else "", max(budget, 0) // world)
+
+    # ---- --full, untimed: where one build's time goes (N > 1, native): one profiled build -------
+    if distributed and not cpu and args.full and not args.no_profile:
         builder.set_profile(True)
         step()
         ph = builder.phases()
@@ -411,7 +494,8 @@ def main(argv=None):
                        "shared_gpu": share and world > 1,
                        "device": "cpu (gloo rehearsal)" if cpu else (
                            f"MI355X (1 GPU shared by {world} ranks)" if share and world > 1 else "MI355X"),
-                       "tree_checked": not args.no_check,
+                       "tree_checked": check,
+                       "build_checked": build_checked,
                        "errors_checked": "every timed build" if (not distributed and not cpu) else
                                          "last build (leaf misses are rebuilt inside each build)",
                        "sampling_misses_rebuilt": misses},

@@ -1,7 +1,8 @@
-"""CLI protocol (Utility.cpp:66-124, kdtree_sequential.cpp:140-208) and byte parity with the
-reference binary compiled from /root/reference (skipped where that tree is absent)."""
+"""CLI protocol (Utility.cpp:66-124, kdtree_sequential.cpp:140-208) and byte parity with what
+the reference binary printed (tests/golden/reference_outputs.json, recorded from the compiled
+reference by oracle/record_golden.py)."""
+import json
 import os
-import shutil
 import subprocess
 from pathlib import Path
 
@@ -9,7 +10,7 @@ import pytest
 
 import parallel_kd_tree_amd as pk
 
-REF = Path("/root/reference")
+GOLDEN = Path(__file__).resolve().parent / "golden" / "reference_outputs.json"
 
 
 def run(exe, args=(), stdin=None, env=None):
@@ -62,27 +63,19 @@ def test_eval_protocol_stdin(bin_dir):
 
 
 @pytest.fixture(scope="module")
-def ref_binary(tmp_path_factory):
-    if not (REF / "kdtree_sequential.cpp").exists() or shutil.which("g++") is None:
-        pytest.skip("reference sources not available")
-    d = tmp_path_factory.mktemp("refbuild")
-    for f in ("kdtree_sequential.cpp", "Node.cpp", "Node.hpp", "Utility.cpp", "Utility.hpp"):
-        (d / f).write_text((REF / f).read_text())
-    src = d / "kdtree_sequential.cpp"
-    src.write_text(src.read_text().replace("#define DEBUG 0", "#define DEBUG 1"))
-    exe = d / "seq_dbg"
-    subprocess.run(["g++", "-O3", "-std=c++17", "-mavx", str(src), str(d / "Node.cpp"), str(d / "Utility.cpp"),
-                    "-o", str(exe)], check=True, capture_output=True)
-    return exe
+def ref_debug():
+    """What the reference's kdtree_sequential.cpp (DEBUG 1) printed, per 'seed_dim_points':
+    stdout lines without the elapsed time, and stderr."""
+    return json.loads(GOLDEN.read_text())["seq_debug"]
 
 
 @pytest.mark.parametrize("cfg", [(42, 3, 1024), (7, 2, 5000), (3, 8, 20000), (11, 1, 777), (2, 3, 100)])
-def test_reference_mode_byte_parity(bin_dir, ref_binary, cfg):
-    a = run(ref_binary, cfg)
+def test_reference_mode_byte_parity(bin_dir, ref_debug, cfg):
+    a = ref_debug["_".join(map(str, cfg))]
     b = run(bin_dir / "kdtree_sequential", ["--mode", "reference", *cfg])
     strip = lambda s: [l for l in s.splitlines() if not l.startswith("elapsed time")]
-    assert strip(a.stdout) == strip(b.stdout)
-    assert a.stderr == b.stderr
+    assert a["stdout"] == strip(b.stdout)
+    assert a["stderr"] == b.stderr
 
 
 @pytest.mark.parametrize("flag", [["--queries", "25"], ["--queries=25"]])

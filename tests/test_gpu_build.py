@@ -429,8 +429,8 @@ def test_bench_native_global_one_rank():
     import sys
     from pathlib import Path
     root = Path(__file__).resolve().parent.parent
-    r = subprocess.run([sys.executable, str(root / "bench.py"), "--decomp", "global", "--points", "3000000", "--steps", "2",
-                        "--warmup", "1", "--pipeline-k", "1"], capture_output=True, text=True, timeout=300)
+    r = subprocess.run([sys.executable, str(root / "bench.py"), "--full", "--decomp", "global", "--points", "3000000",
+                        "--steps", "2", "--warmup", "1", "--pipeline-k", "1"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line["config"]["parallelism"] == "global1" and line["config"]["tree_checked"]

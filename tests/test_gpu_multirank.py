@@ -144,7 +144,7 @@ def test_bench_rccl_share_gpu(gpus):
     """bench.py --gpus N on one card (the rehearsal mode of the driver's multi-GPU run): one JSON
     line from rank 0, the tree checked across ranks, the per-phase breakdown on stderr."""
     env = dict(os.environ, PKD_BENCH_SHARE_GPU="1")
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", str(gpus), "--points", "2000000",
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--full", "--gpus", str(gpus), "--points", "2000000",
                         "--steps", "2", "--warmup", "1"], capture_output=True, text=True, timeout=240, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])

@@ -1,4 +1,7 @@
-"""Byte parity with the REAL reference binaries, compiled here from /root/reference.
+"""Byte parity with what the REAL reference binaries printed.
+
+tests/golden/reference_outputs.json holds the output of the reference programs, compiled from
+their unchanged sources and run at the configurations below by oracle/record_golden.py:
 
 * kdtree_sequential.cpp, unmodified (DEBUG 0): the graded evaluation path (seed on stdin,
   500 000 x 128, Utility.cpp:92-102). At d=128 the reference search is exact, so
@@ -9,10 +12,10 @@
   low-dimensional configs, where its forest gives different answers than the sequential
   binary that our `--decomp forest --mode reference` must reproduce exactly.
 * tests/fixtures/ref_eval_seed*.txt hold the unmodified reference's eval-mode stdout; they
-  are checked against the compiled reference here and used by the GPU tests (test_gpu_cli.py),
-  which run where /root/reference does not exist.
-Skipped where /root/reference is absent.
+  are checked against the recorded reference output here and used by the GPU tests
+  (test_gpu_cli.py).
 """
+import json
 import os
 import socket
 import subprocess
@@ -21,12 +24,9 @@ from pathlib import Path
 
 import pytest
 
-REF = Path("/root/reference")
 ROOT = Path(__file__).resolve().parent.parent
 FIX = Path(__file__).resolve().parent / "fixtures"
-pytestmark = pytest.mark.skipif(not (REF / "kdtree_sequential.cpp").exists(), reason="reference sources not available")
-
-GXX = ["g++", "-O3", "-std=c++17", "-mavx"]  # the reference Makefile's flags (Makefile:1-2)
+GOLDEN = Path(__file__).resolve().parent / "golden" / "reference_outputs.json"
 
 
 def _run(cmd, stdin=None, env=None, timeout=600):
@@ -34,45 +34,13 @@ def _run(cmd, stdin=None, env=None, timeout=600):
 
 
 @pytest.fixture(scope="module")
-def ref_seq(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("ref") / "sequential"
-    subprocess.run([*GXX, "-I", REF, REF / "kdtree_sequential.cpp", REF / "Node.cpp", REF / "Utility.cpp", "-o", exe],
-                   check=True, capture_output=True)
-    return exe
+def ref():
+    """The reference programs' recorded output: ref[program][configuration]."""
+    return json.loads(GOLDEN.read_text())
 
 
-def _build_mpi(d: Path, debug: bool) -> Path:
-    src = REF / "kdtree_mpi.cpp"
-    if debug:
-        text = src.read_text().replace("#define DEBUG 0", "#define DEBUG 1", 1)
-        # F6: `tick` is declared inside the rank-0 block and used in another one
-        text = text.replace("auto tick = std::chrono::high_resolution_clock::now();", "tick = std::chrono::high_resolution_clock::now();", 1)
-        text = text.replace("int data[3];", "int data[3];\n    auto tick = std::chrono::high_resolution_clock::now();", 1)
-        src = d / "kdtree_mpi_debug.cpp"
-        src.write_text(text)
-    exe = d / ("mpi_debug" if debug else "mpi")
-    r = _run([*GXX, "-I", REF, "-I", Path(__file__).parent / "fakempi", src, REF / "Node.cpp", REF / "Utility.cpp",
-              "-o", exe])
-    assert r.returncode == 0, r.stderr
-    return exe
-
-
-@pytest.fixture(scope="module")
-def ref_mpi(tmp_path_factory):
-    d = tmp_path_factory.mktemp("refmpi")
-    return {False: _build_mpi(d, False), True: _build_mpi(d, True)}
-
-
-def _run_mpi(exe, P, tmp, args=(), stdin=None):
-    """P processes of the reference MPI driver; rank 0's stdout."""
-    procs = []
-    for r in range(P):
-        env = dict(os.environ, FAKEMPI_RANK=str(r), FAKEMPI_SIZE=str(P), FAKEMPI_DIR=str(tmp))
-        procs.append(subprocess.Popen([str(exe), *map(str, args)], stdin=subprocess.PIPE, stdout=subprocess.PIPE,
-                                      stderr=subprocess.PIPE, text=True, env=env))
-    outs = [p.communicate(input=(stdin if r == 0 else ""), timeout=600) for r, p in enumerate(procs)]
-    assert all(p.returncode == 0 for p in procs), [o[1] for o in outs]
-    return outs[0]
+def _key(*parts):
+    return "_".join(str(p) for p in parts)
 
 
 def _free_port():
@@ -100,57 +68,48 @@ def _results(stdout):
 
 @pytest.mark.slow
 @pytest.mark.parametrize("seed", [3, 42])
-def test_eval_config_byte_parity(ref_seq, bin_dir, seed):
-    ref = _run([ref_seq], stdin=f"{seed}\n")
-    assert ref.returncode == 0
+def test_eval_config_byte_parity(ref, bin_dir, seed):
+    want = ref["seq_eval"][_key(seed)]
     for mode in ("exact", "reference"):
         ours = _run([bin_dir / "kdtree_sequential", "--threads", "8", "--mode", mode], stdin=f"{seed}\n")
         assert ours.returncode == 0, ours.stderr
-        assert ours.stdout == ref.stdout, mode
-        assert ours.stderr == ref.stderr, mode
+        assert ours.stdout == want["stdout"], mode
+        assert ours.stderr == want["stderr"], mode
     fix = FIX / f"ref_eval_seed{seed}.txt"
-    assert fix.read_text() == ref.stdout, "fixture differs from the compiled reference"
+    assert fix.read_text() == want["stdout"], "fixture differs from the recorded reference output"
 
 
 @pytest.mark.parametrize("cfg", [(42, 3, 1024), (1, 2, 1), (5, 8, 3000)])
-def test_debug_config_byte_parity_exact_points(ref_seq, bin_dir, tmp_path, cfg):
+def test_debug_config_byte_parity_exact_points(ref, bin_dir, cfg):
     """Unmodified DEBUG 0 binary cannot take argv; its eval path is covered above. Here the
     same sources with DEBUG 1: reference mode is byte-identical (elapsed time aside)."""
-    src = tmp_path / "kdtree_sequential.cpp"
-    src.write_text((REF / "kdtree_sequential.cpp").read_text().replace("#define DEBUG 0", "#define DEBUG 1", 1))
-    exe = tmp_path / "seq_dbg"
-    subprocess.run([*GXX, "-I", REF, src, REF / "Node.cpp", REF / "Utility.cpp", "-o", exe], check=True,
-                   capture_output=True)
-    ref = _run([exe, *cfg])
+    want = ref["seq_debug"][_key(*cfg)]
     ours = _run([bin_dir / "kdtree_sequential", "--mode", "reference", *cfg])
-    assert _results(ours.stdout) == _results(ref.stdout) and ours.stderr == ref.stderr
+    assert _results(ours.stdout) == want["stdout"] and ours.stderr == want["stderr"]
 
 
 @pytest.mark.slow
 @pytest.mark.parametrize("P", [2, 4])
-def test_mpi_eval_config_parity(ref_mpi, tmp_path, P):
+def test_mpi_eval_config_parity(ref, P):
     """The unmodified reference MPI driver at its evaluation config (stdin seed, 500k x 128)."""
-    out, _ = _run_mpi(ref_mpi[False], P, tmp_path, stdin="7\n")
-    assert _results(_ours_forest(P, [7, 128, 500000])) == _results(out)
+    assert _results(_ours_forest(P, [7, 128, 500000])) == ref["mpi_eval"][_key(P, 7)]
 
 
 @pytest.mark.parametrize("P,cfg", [(2, (42, 3, 20000)), (4, (11, 3, 20000)), (4, (5, 2, 7001)), (3, (9, 8, 5000))])
-def test_mpi_forest_parity_low_dim(ref_mpi, tmp_path, P, cfg):
+def test_mpi_forest_parity_low_dim(ref, P, cfg):
     """Low dims, where the reference forest's answers differ from the sequential binary's and
     from brute force (F1/F2): ours must print exactly the reference MPI driver's lines."""
-    out, _ = _run_mpi(ref_mpi[True], P, tmp_path, args=cfg)
-    lines = _results(out)
+    lines = ref["mpi_debug"][_key(P, *cfg)]
     assert lines[0] == "READY" and lines[-1] == "DONE" and len(lines) == 12
     assert _results(_ours_forest(P, cfg)) == lines
 
 
 @pytest.mark.parametrize("procs,cfg", [(2, (42, 3, 20000)), (1, (7, 2, 9001)), (3, (5, 3, 16003))])
-def test_mpi_16_ranks_on_fewer_processes(ref_mpi, tmp_path, procs, cfg):
+def test_mpi_16_ranks_on_fewer_processes(ref, procs, cfg):
     """The reference's own launch, `mpirun -np 16 --oversubscribe` (Makefile:36), reproduced by
     fewer processes (GPUs): --ranks 16 spreads the 16 logical forest ranks over them, each keeping
     the reference's slicing at P = 16, so reference-mode answers (which depend on P)
     equal the reference MPI driver's at 16 processes, byte for byte."""
-    out, _ = _run_mpi(ref_mpi[True], 16, tmp_path, args=cfg)
-    lines = _results(out)
+    lines = ref["mpi_debug"][_key(16, *cfg)]
     assert lines[0] == "READY" and lines[-1] == "DONE" and len(lines) == 12
     assert _results(_ours_forest(procs, cfg, extra=["--ranks", "16"])) == lines

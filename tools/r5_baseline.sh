@@ -7,7 +7,7 @@ O=gpurun_out/r5_baseline
 mkdir -p $O
 run() {  # tag, then bench.py arguments
   local tag=$1; shift
-  PKD_SKIP_BUILD=1 timeout -k 10 240 python3 -u bench.py "$@" > $O/$tag.log 2>&1 || return 1
+  PKD_SKIP_BUILD=1 timeout -k 10 240 python3 -u bench.py --full "$@" > $O/$tag.log 2>&1 || return 1
   grep -h '"metric"' $O/$tag.log | sed "s/^/$tag /" >> $O/all.txt
 }
 : > $O/all.txt
