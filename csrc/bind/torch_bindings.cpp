@@ -8,7 +8,9 @@
 #include <algorithm>
 #include <memory>
 #include <sstream>
+#include <stdexcept>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "pkdtree/common.hpp"
@@ -16,6 +18,7 @@
 #include "pkdtree/generator.hpp"
 #include "pkdtree/gpu_build.hpp"
 #include "pkdtree/gpu_generator.hpp"
+#include "pkdtree/gpu_knn.hpp"
 #include "pkdtree/gpu_query.hpp"
 #include "pkdtree/gpu_reference.hpp"
 #include "pkdtree/trace.hpp"
@@ -353,6 +356,96 @@ std::vector<torch::Tensor> nn_finalize(const torch::Tensor& packed) {
   return {d, i};
 }
 
+void check_k(int64_t k) {
+  if (k < 1 || k > pk::kKnnMax) throw std::invalid_argument("k must be in 1..64, got " + std::to_string(k));
+}
+
+// Packed k-NN lists (gpu_knn.hpp): int64 [nq, k], ascending rows, padded with kPackedInf. With
+// `into` the search starts from (and returns) that tensor's sorted rows.
+torch::Tensor knn_gpu(const torch::Tensor& pts, const c10::optional<torch::Tensor>& ids, int64_t id_base,
+                      const torch::Tensor& queries, int64_t k, const std::string& method, int64_t depth0,
+                      c10::optional<torch::Tensor> into) {
+  check_k(k);
+  check_points(pts, true);
+  check_points(queries, true);
+  TORCH_CHECK(queries.size(1) == pts.size(1), "dimension mismatch");
+  TORCH_CHECK(queries.device() == pts.device(), "queries must be on the tree's device");
+  const c10::DeviceGuard guard(pts.device());
+  const int64_t nq = queries.size(0), n = pts.size(0);
+  hipStream_t s = cur_stream(pts);
+  torch::Tensor out;
+  if (into.has_value()) {
+    out = *into;
+    TORCH_CHECK(out.scalar_type() == torch::kInt64 && out.dim() == 2 && out.size(0) == nq && out.size(1) == k &&
+                    out.is_contiguous() && out.device() == pts.device(),
+                "`into` must be a contiguous int64 [nq, k] tensor on the tree's device");
+  } else {
+    out = torch::empty({nq, k}, queries.options().dtype(torch::kInt64));
+    pk::nn_init(reinterpret_cast<pk::u64*>(out.data_ptr<int64_t>()), nq * k, s);
+  }
+  auto* o = reinterpret_cast<pk::u64*>(out.data_ptr<int64_t>());
+  const pk::u32* idp = opt_ids(ids, n, pts.device());
+  if (method == "brute") {
+    torch::Tensor scratch = torch::empty({int64_t(pk::knn_brute_scratch_words(n, nq, int(k)))},
+                                         queries.options().dtype(torch::kInt64));
+    pk::knn_brute(pts.data_ptr<float>(), idp, pk::u32(id_base), n, int(pts.size(1)), queries.data_ptr<float>(), nq,
+                  int(k), o, s, reinterpret_cast<pk::u64*>(scratch.data_ptr<int64_t>()));
+  } else if (method == "traverse") {
+    TORCH_CHECK(idp != nullptr, "traverse needs the tree ids");
+    pk::knn_traverse(pts.data_ptr<float>(), idp, n, int(pts.size(1)), int(depth0), queries.data_ptr<float>(), nq,
+                     int(k), o, s);
+  } else {
+    TORCH_CHECK(false, "method must be 'brute' or 'traverse'");
+  }
+  return out;
+}
+
+// The CPU oracle (cpu_tree.hpp knn_brute_cpu), threaded over the queries.
+torch::Tensor knn_cpu(const torch::Tensor& pts, const c10::optional<torch::Tensor>& ids, int64_t id_base,
+                      const torch::Tensor& queries, int64_t k) {
+  check_k(k);
+  check_points(pts, false);
+  check_points(queries, false);
+  TORCH_CHECK(queries.size(1) == pts.size(1), "dimension mismatch");
+  const int64_t nq = queries.size(0), n = pts.size(0);
+  const int dim = int(pts.size(1));
+  const pk::u32* idp = opt_ids(ids, n, pts.device());
+  torch::Tensor out = torch::empty({nq, k}, torch::kInt64);
+  auto* o = reinterpret_cast<pk::u64*>(out.data_ptr<int64_t>());
+  const float* p = pts.data_ptr<float>();
+  const float* q = queries.data_ptr<float>();
+  auto run = [&](int64_t a, int64_t b) {
+    for (int64_t i = a; i < b; ++i) pk::knn_brute_cpu(p, idp, pk::u32(id_base), n, dim, q + i * dim, int(k), o + i * k);
+  };
+  const int64_t threads = std::min<int64_t>({int64_t(pk::default_cpu_threads()), 16, nq, n * nq / 1000000 + 1});
+  if (threads <= 1) {
+    run(0, nq);
+    return out;
+  }
+  py::gil_scoped_release nogil;
+  std::vector<std::thread> pool;
+  for (int64_t t = 0; t < threads; ++t) pool.emplace_back(run, nq * t / threads, nq * (t + 1) / threads);
+  for (auto& t : pool) t.join();
+  return out;
+}
+
+// The k smallest of two sorted [nq, k] lists of disjoint point sets, per row.
+torch::Tensor knn_merge(const torch::Tensor& a, const torch::Tensor& b) {
+  TORCH_CHECK(a.scalar_type() == torch::kInt64 && a.dim() == 2 && a.is_contiguous(), "a must be contiguous int64 [nq, k]");
+  TORCH_CHECK(b.scalar_type() == torch::kInt64 && b.sizes() == a.sizes() && b.is_contiguous() &&
+                  b.device() == a.device(), "b must be a contiguous int64 tensor shaped like a, on its device");
+  const int64_t nq = a.size(0), k = a.size(1);
+  check_k(k);
+  if (!a.is_cuda())  // bit 63 is never set, so the signed sort is the unsigned order
+    return std::get<0>(torch::cat({a, b}, 1).sort(1)).slice(1, 0, k).contiguous();
+  const c10::DeviceGuard guard(a.device());
+  torch::Tensor out = torch::empty_like(a);
+  pk::knn_merge(reinterpret_cast<const pk::u64*>(a.data_ptr<int64_t>()),
+                reinterpret_cast<const pk::u64*>(b.data_ptr<int64_t>()), nq, int(k),
+                reinterpret_cast<pk::u64*>(out.data_ptr<int64_t>()), cur_stream(a));
+  return out;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -449,6 +542,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("nn", &nn_gpu, py::arg("points"), py::arg("ids"), py::arg("id_base"), py::arg("queries"),
         py::arg("method") = "brute", py::arg("depth0") = 0, py::arg("into") = c10::nullopt);
   m.def("nn_finalize", &nn_finalize, py::arg("packed"));
+  m.def("knn", &knn_gpu, py::arg("points"), py::arg("ids"), py::arg("id_base"), py::arg("queries"), py::arg("k"),
+        py::arg("method") = "brute", py::arg("depth0") = 0, py::arg("into") = c10::nullopt);
+  m.def("knn_cpu", &knn_cpu, py::arg("points"), py::arg("ids"), py::arg("id_base"), py::arg("queries"), py::arg("k"));
+  m.def("knn_merge", &knn_merge, py::arg("a"), py::arg("b"));
   m.def("subtree_capacity", &pk::default_subtree_max);
   m.def("subtree_stamp_report", &pk::subtree_stamp_report);
   m.def("tail_stamp_report", &pk::tail_stamp_report);

@@ -2,6 +2,7 @@
 #include "pkdtree/cpu_tree.hpp"
 
 #include <algorithm>
+#include <stdexcept>
 #include <thread>
 #include <unordered_set>
 #include <vector>
@@ -369,6 +370,26 @@ NNResult nn_brute_cpu(const float* pts, i64 n, int dim, const float* q) {
     if (r.slot < 0 || d < r.d2) r = {i, d};
   }
   return r;
+}
+
+void knn_brute_cpu(const float* pts, const u32* ids, u32 id_base, i64 n, int dim, const float* q, int k, u64* out) {
+  if (k < 1 || k > 64) throw std::invalid_argument("knn_brute_cpu: k must be in 1..64");
+  u64 heap[64];  // bounded max-heap of the k smallest packed values so far
+  int m = 0;
+  for (i64 i = 0; i < n; ++i) {
+    const u64 v = pack_dist_idx(sq_dist(pts + size_t(i) * size_t(dim), q, dim), ids ? ids[i] : id_base + u32(i));
+    if (m < k) {
+      heap[m++] = v;
+      std::push_heap(heap, heap + m);
+    } else if (v < heap[0]) {
+      std::pop_heap(heap, heap + m);
+      heap[m - 1] = v;
+      std::push_heap(heap, heap + m);
+    }
+  }
+  std::sort_heap(heap, heap + m);
+  std::copy(heap, heap + m, out);
+  std::fill(out + m, out + k, kPackedInf);
 }
 
 i64 count_invariant_violations(const float* tree_pts, const u32* tree_ids, i64 n, int dim, int depth0) {

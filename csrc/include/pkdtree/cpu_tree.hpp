@@ -57,6 +57,11 @@ struct NNResult {
 NNResult nn_search_cpu(const float* tree_pts, i64 n, int dim, int depth0, const float* q);
 // Exact brute force: lexicographic (d2, slot) minimum.
 NNResult nn_brute_cpu(const float* pts, i64 n, int dim, const float* q);
+// Exact k-NN brute force of one query (the oracle of the GPU k-NN kernels, gpu_knn.hpp): out[0, k)
+// = the k smallest pack_dist_idx(sq_dist(point, q), id) in ascending order, kPackedInf where
+// fewer than k points exist. ids may be null (id = id_base + row). 1 <= k <= 64, else
+// std::invalid_argument.
+void knn_brute_cpu(const float* pts, const u32* ids, u32 id_base, i64 n, int dim, const float* q, int k, u64* out);
 
 // Number of violations of the exact-mode invariant: for every node, every element of the
 // left subtree is < the node and every element of the right subtree is > the node under

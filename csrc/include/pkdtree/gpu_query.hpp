@@ -10,6 +10,7 @@
 // (distance, id) minimum, so results from different ranks/trees combine with one MIN
 // reduction (the reference's MPI_Reduce(MIN), kdtree_mpi.cpp:253, but carrying the id).
 // Distances use the reference's summation order (see common.hpp).
+// (k nearest neighbours with the same packing and order: gpu_knn.hpp.)
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -146,6 +146,42 @@ class KDTree:
         # distance printed by the reference: sqrt(distance_squared(query, nn)), computed in fp32
         return ops.query.sqrt_exact(d2), ids
 
+    def knn_packed(self, queries: torch.Tensor, k: int, method: str = "auto",
+                   into: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Exact k nearest neighbours, packed: int64 [nq, k], every row the k smallest
+        (d2, id) in ascending order (ties on distance -> smaller id; column 0 is the 1-NN
+        answer), padded with ``ops.query.INF_PACKED`` where the tree has fewer than k points.
+
+        ``method``: auto (traverse for dim <= 16, else brute) | brute | traverse (dim <= 32). A
+        reference-mode tree always uses brute force (it violates the kd invariant; brute force is
+        exact on any layout) and a CPU tree the host brute force. ``into`` ([nq, k] sorted rows
+        on the tree's device) is the starting list, updated in place and returned: chain it
+        across trees of DISJOINT point sets (forest slices); searching the same tree twice
+        into one list duplicates its entries."""
+        k = ops.query._check_k(k)
+        if method not in ("auto", "brute", "traverse"):
+            raise ValueError("method must be 'auto', 'brute' or 'traverse'")
+        if method == "traverse" and self.dim > 32:
+            raise ValueError("k-NN traversal needs dim <= 32; use method='brute'")
+        if not self.tree_pts.is_cuda:
+            res = ops.knn_cpu(self.tree_pts, self.tree_ids, queries, k)
+            if into is None:
+                return res
+            if into.dtype != torch.int64 or tuple(into.shape) != tuple(res.shape) or into.is_cuda:
+                raise ValueError("`into` must be an int64 [nq, k] tensor on the tree's device")
+            return into.copy_(ops.knn_merge(into, res))
+        q = queries.to(self.device, torch.float32).contiguous()
+        if self.mode == "reference":
+            method = "brute"
+        elif method == "auto":
+            method = "traverse" if self.dim <= 16 else "brute"
+        return ops.knn_gpu(self.tree_pts, self.tree_ids, q, k, method, self.depth0, 0, into)
+
+    def knn(self, queries: torch.Tensor, k: int, method: str = "auto") -> Tuple[torch.Tensor, torch.Tensor]:
+        """Exact k nearest neighbours: (distance float32 [nq, k], id int64 [nq, k]), ascending
+        by (distance, id); rows of a tree with fewer than k points end in ``inf`` / ``-1``."""
+        return ops.finalize_knn(self.knn_packed(queries, k, method))
+
     def nearest_neighbor(self, query: Point) -> Optional[Node]:
         """Reference API (kdtree_sequential.cpp:133-136): the Node of the nearest point."""
         if self.n == 0:

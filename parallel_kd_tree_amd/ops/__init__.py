@@ -31,5 +31,7 @@ from .build import (GpuTreeBuilder, ReferenceTreeBuilder, build_cpu, build_gpu, 
                     build_reference_gpu_checked,  # noqa: E402
                     gpu_builder, reference_builder)
 from .query import nn_gpu, unpack, finalize, nn_cpu  # noqa: E402
+from .query import knn_gpu, knn_cpu, knn_merge, finalize_knn  # noqa: E402
 
-__all__ = ["native", "native_path", "GpuTreeBuilder", "build_gpu", "build_gpu_checked", "build_cpu", "check_unique_ids", "gpu_builder", "nn_gpu", "unpack", "finalize", "nn_cpu"]
+__all__ = ["native", "native_path", "GpuTreeBuilder", "build_gpu", "build_gpu_checked", "build_cpu", "check_unique_ids", "gpu_builder", "nn_gpu", "unpack", "finalize", "nn_cpu",
+           "knn_gpu", "knn_cpu", "knn_merge", "finalize_knn"]

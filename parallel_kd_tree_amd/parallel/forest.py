@@ -12,6 +12,7 @@ from typing import Optional
 
 import torch
 
+from .. import ops
 from ..models.kdtree import KDTree
 from . import comm
 from .global_tree import _local_packed
@@ -43,6 +44,18 @@ class ForestTree:
         """Packed (d2, global id) of the nearest point over all ranks. Reference-mode forests
         use the reference search on each rank (so results match kdtree_mpi exactly)."""
         return comm.min_packed_(self.local_packed(queries, method).to(comm.device()))
+
+    def knn_packed(self, queries: torch.Tensor, k: int, method: str = "auto") -> torch.Tensor:
+        """Packed k nearest neighbours over all ranks (``KDTree.knn_packed``'s [nq, k] rows of
+        global ids): every rank's local list is all-gathered and the lists, which come from
+        disjoint slices, are merged. Ranks without points contribute padding only."""
+        local = self.local.knn_packed(queries, k, method).to(comm.device()).contiguous()
+        lists = torch.empty((comm.world(),) + tuple(local.shape), dtype=torch.int64, device=local.device)
+        comm.all_gather_into_(lists, local)
+        best = lists[0]
+        for r in range(1, comm.world()):
+            best = ops.knn_merge(best, lists[r])
+        return best
 
 
 def logical_ranks(ranks: int, world: int, rank: int) -> range:

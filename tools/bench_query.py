@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Warm timing of the exact 1-NN kernels on one GPU: brute force and traversal over the
-reference generator's points (default: the reference's eval config, 500k x 128D, 10 queries)."""
+reference generator's points (default: the reference's eval config, 500k x 128D, 10 queries).
+With --k K the exact k-NN kernels (KDTree.knn_packed) are timed in the same process, beside them."""
 import argparse
 import json
 import os
@@ -17,6 +18,7 @@ ap.add_argument("--n", type=int, default=500_000)
 ap.add_argument("--dim", type=int, default=128)
 ap.add_argument("--queries", type=int, default=10)
 ap.add_argument("--reps", type=int, default=20)
+ap.add_argument("--k", type=int, default=0, help="also time KDTree.knn_packed at this k (brute and traverse)")
 args = ap.parse_args()
 dev = torch.device("cuda:0")
 x = pk.generate_slice(42, args.dim, 0, args.n + args.queries, device=dev)
@@ -50,4 +52,33 @@ for method in methods:
     res[method + "_dev_ms"] = round(e0.elapsed_time(e1) / args.reps, 4)
 if "traverse" in out:
     res["same"] = bool(torch.equal(out["brute"], out["traverse"]))
+if args.k:
+    # k-NN (KDTree.knn_packed) beside the 1-NN lines of the same process: device time around a
+    # re-initialised list, like the 1-NN `_dev_ms`. The brute force is the fallback, not a hot
+    # path: it gets a tenth of the repetitions.
+    res["k"] = args.k
+    kout = {}
+    for method in methods:
+        reps = args.reps if method == "traverse" else max(1, args.reps // 10)
+        into = torch.empty((q.shape[0], args.k), dtype=torch.int64, device=dev)
+        for _ in range(2):
+            kout[method] = tree.knn_packed(q, args.k, method)
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            into.fill_(ops.query.INF_PACKED)
+            tree.knn_packed(q, args.k, method, into)
+        e1.record()
+        torch.cuda.synchronize()
+        res[f"knn_{method}_dev_ms"] = round(e0.elapsed_time(e1) / reps, 4)
+        if not torch.equal(into, kout[method]):
+            raise SystemExit(f"k-NN {method}: the timed result differs from the warm-up's")
+    if "traverse" in kout:
+        res["knn_same"] = bool(torch.equal(kout["brute"], kout["traverse"]))
+        if "traverse_dev_ms" in res:
+            res["knn_traverse_over_1nn_traverse"] = round(res["knn_traverse_dev_ms"] / res["traverse_dev_ms"], 3)
+        res["knn_brute_over_knn_traverse"] = round(res["knn_brute_dev_ms"] / res["knn_traverse_dev_ms"], 1)
+    if args.k == 1:
+        res["knn_col0_is_1nn"] = bool(torch.equal(kout[methods[-1]][:, 0], out[methods[-1]]))
 print(json.dumps(res), flush=True)
